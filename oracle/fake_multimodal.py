@@ -53,7 +53,7 @@ def loaders(seed: int = 11):
 
 class OracleMultiModalGB(nn.Module):
     """Test infrastructure: oracle.multimodal's functional MultiModalModel_GB restatement (itself pinned by
-    tests/golden/multimodal.npz) behind the module interface the Gradient-Blending loops need -- parameters that an optimizer can
+    tests/golden/multimodal_gb.npz) behind the module interface the Gradient-Blending loops need -- parameters that an optimizer can
     step, state_dict()/load_state_dict() for the checkpoint reload, update_use_stream() and the four forward variants of the
     reference (src/models/MultiModal.py:131-149).  Built from a state dict with the reference's keys; float64 on the CPU."""
 

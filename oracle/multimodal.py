@@ -1,6 +1,6 @@
 """CPU restatement (test infrastructure only) of the reference's fusion wrappers (src/models/MultiModal.py): MultiModalModel
 (:33-39), MultiModalModel_GB.forward_stream (:131-149), TFN (:213-224) and TFN_GB (:294-311) as functions of a state dict with the
-reference's keys, on top of oracle.vivit and oracle.transformer0d (noise std 0, dropout 0).  Pinned by tests/golden/multimodal.npz."""
+reference's keys, on top of oracle.vivit and oracle.transformer0d (noise std 0, dropout 0).  Pinned by tests/golden/multimodal_*.npz."""
 import torch
 import torch.nn.functional as F
 

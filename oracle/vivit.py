@@ -1,6 +1,6 @@
 """CPU restatement (test infrastructure only) of the reference's ViViT.forward / ViViTEncoder.forward (src/models/ViViT.py:171-194,
 284-299) as a function of a state dict with the reference's keys (dropout 0).  The einops patterns are written out as
-reshape / permute.  Pinned by tests/golden/vivit.npz."""
+reshape / permute.  Pinned by tests/golden/vivit_*.npz."""
 import torch
 import torch.nn.functional as F
 

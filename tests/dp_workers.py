@@ -234,6 +234,9 @@ def loop_worker(rank, world, port, out_dir):
     exchange is covered by gpu_worker)."""
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     from src import distributed as D
+    # the loop's CPU leg (gloo, torch AdamW) is what this worker covers, also where a GPU is visible: there train_per_proc would
+    # take its RCCL leg and put rank r on cuda:r, which a one-GPU machine does not have (this process only)
+    torch.cuda.is_available = lambda: False
     torch.manual_seed(1000 + rank)                          # different init per rank: the broadcast must fix it
     model = torch.nn.Sequential(torch.nn.Linear(6, 8), torch.nn.Tanh(), torch.nn.Linear(8, 2))
     train = LoggedDataset(24, nan_index=5, seed=1); valid = LoggedDataset(8, seed=2)

@@ -469,7 +469,8 @@ def vivit_fixture():
         for k, p in m.named_parameters():
             rec[tag + "/grad/" + k] = p.grad.numpy()
         print("vivit", tag, out.detach().numpy().ravel()[:4])
-    np.savez_compressed(os.path.join(HERE, "vivit.npz"), **rec)
+    for tag in ("cls", "enc"):          # one file per case, so that each stays under 1 MiB
+        np.savez_compressed(os.path.join(HERE, "vivit_%s.npz" % tag), **{k: v for k, v in rec.items() if k.split("/")[0] == tag})
 
 
 def multimodal_fixture():
@@ -517,7 +518,8 @@ def multimodal_fixture():
             if "running" in k:
                 rec[tag + "/after/" + k] = t.numpy()
         print("multimodal", tag, [o.detach().numpy().ravel()[:2] for o in outs])
-    np.savez_compressed(os.path.join(HERE, "multimodal.npz"), **rec)
+    for tag in ("mm", "gb", "tfn", "tfngb"):          # one file per case, so that each stays under 1 MiB
+        np.savez_compressed(os.path.join(HERE, "multimodal_%s.npz" % tag), **{k: v for k, v in rec.items() if k.split("/")[0] == tag})
 
 
 def fusion_derived_fixture():

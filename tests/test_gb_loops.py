@@ -87,7 +87,7 @@ A0 = dict(n_features=6, kernel_size=3, feature_dims=16, max_len=5, n_layers=1, n
 def _native_and_oracle(golden_dir):
     from oracle.fake_multimodal import OracleMultiModalGB
     from src.models.MultiModal import MultiModalModel_GB
-    g = np.load(os.path.join(golden_dir, "multimodal.npz"))
+    g = np.load(os.path.join(golden_dir, "multimodal_gb.npz"))
     sd = {k[len("gb/sd/"):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("gb/sd/")}
     m = MultiModalModel_GB(2, dict(AV), dict(A0))
     m.load_state_dict(sd, strict=True)

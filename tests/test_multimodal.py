@@ -23,7 +23,7 @@ CASES = {"mm": ("MultiModalModel", dict(AV, pool="mean"), A0, om.multimodal_forw
 
 
 def _load(golden_dir, tag):
-    g = np.load(os.path.join(golden_dir, "multimodal.npz"))
+    g = np.load(os.path.join(golden_dir, "multimodal_%s.npz" % tag))
     pre = tag + "/sd/"
     return g, {k[len(pre):]: torch.from_numpy(g[k]) for k in g.files if k.startswith(pre)}
 

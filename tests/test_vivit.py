@@ -18,7 +18,7 @@ CASES = {"cls": ("ViViT", dict(n_classes=2, pool="cls", alpha=0.7)), "enc": ("Vi
 
 
 def _load(golden_dir, tag):
-    g = np.load(os.path.join(golden_dir, "vivit.npz"))
+    g = np.load(os.path.join(golden_dir, "vivit_%s.npz" % tag))
     pre = tag + "/sd/"
     return g, {k[len(pre):]: torch.from_numpy(g[k]) for k in g.files if k.startswith(pre)}
 
