@@ -99,14 +99,23 @@ class Attention(nn.Module):
         self.scale = d_head ** (-0.5)
 
         self.to_qkv = nn.Linear(dim, self.inner_dim * 3, bias=False)
+        # set only while src.visualization.visualize_attention.ViViTAttentionRollout records a forward: called with (self, qkv)
+        self._xai_recorder = None
         self.to_out = nn.Sequential(
             nn.Linear(self.inner_dim, dim),
             nn.Dropout(dropout)
         ) if project_out else nn.Identity()
 
+    def _qkv(self, x: torch.Tensor):
+        qkv = _rows(x, self.to_qkv)
+        rec = getattr(self, "_xai_recorder", None)
+        if rec is not None:
+            rec(self, qkv)
+        return qkv
+
     def forward(self, x: torch.Tensor):
         # x (b, n, dim); q | k | v in thirds of the projection, heads as 'b n (h d)' (reference :72-76)
-        out = AttentionFunction.apply(_rows(x, self.to_qkv), None, self.n_heads, None, True)
+        out = AttentionFunction.apply(self._qkv(x), None, self.n_heads, None, True)
         if isinstance(self.to_out, nn.Identity):
             return out
         return dropout(_rows(out, self.to_out[0]), self.to_out[1].p, self.to_out[1].training)
@@ -115,7 +124,7 @@ class Attention(nn.Module):
         """As FeedForward.branch_tail; None when there is no output projection (then forward() is the whole branch)."""
         if isinstance(self.to_out, nn.Identity):
             return None
-        out = AttentionFunction.apply(_rows(x, self.to_qkv), None, self.n_heads, None, True)
+        out = AttentionFunction.apply(self._qkv(x), None, self.n_heads, None, True)
         lin = self.to_out[0]
         return LinearRowsFunction.apply(out.reshape(-1, out.shape[-1]), lin.weight), lin.bias, self.to_out[1].p, self.to_out[1].training
 

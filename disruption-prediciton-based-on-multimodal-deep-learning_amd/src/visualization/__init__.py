@@ -1,0 +1,7 @@
+"""Explainability tools of the reference's ``src/visualization`` on the MI355X: ``visualize_cam.GradCAM_R2Plus1D`` and
+``visualize_attention.ViViTAttentionRollout`` (maps computed by the gfx950 kernels of csrc/xai.hip, batched over clips)."""
+import os as _os
+
+_ref = _os.environ.get("MD_REFERENCE_SRC")
+if _ref and _os.path.isdir(_os.path.join(_ref, "visualization")):
+    __path__.append(_os.path.join(_ref, "visualization"))

@@ -552,6 +552,44 @@ typedef struct MdTrainStepArgs {
 } MdTrainStepArgs;
 int md_plan_train_step(MdPlan* plan, const MdTrainStepArgs* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Explainability maps (csrc/xai.hip): Grad-CAM for R(2+1)D (src/visualization/visualize_cam.py:57-132) and attention rollout
+ * for ViViT (src/visualization/visualize_attention.py:28-135), batched over clips.
+ * ---------------------------------------------------------------------------------------------- */
+/* d logit[b, target[b]] / d feat[b, :] of the classifier head in eval mode (R2Plus1D.py:243-248; visualize_cam.py:84-85 takes
+ * it through score.backward()): Linear(D->Hd) -> BatchNorm1d with running statistics -> activation -> Linear(Hd->K), i.e.
+ * W0^T ((W1[target] * act'(h)) * gamma / sqrt(rvar + eps)).  Activation as md_head_fwd: elu_alpha >= 0 -> ELU(elu_alpha),
+ * < 0 -> LeakyReLU(-elu_alpha).  target: B int64 on the device; a clip whose target lies outside [0, K) gets a NaN row.
+ * (D + Hd) * 4 bytes of LDS: D + Hd <= 16384. */
+int md_head_eval_dfeat(const float* feat, int32_t B, int32_t D, int32_t Hd, int32_t K, const float* w0, const float* b0,
+                       const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps, float elu_alpha,
+                       const float* w1, const int64_t* target, float* dfeat, void* stream);
+/* Grad-CAM map (visualize_cam.py:87-103) from the trunk's last materialised activation act [B*T'*h*w][Cpad] (channels-last, the
+ * tensor md_avgpool_fwd reads; md_plan_z_layout of the last z).  The pool is the only op after it, so the gradient there is
+ * dfeat / (T'*h*w) everywhere and the channel weights are alpha[b][c] = dfeat[b][c] / (T'*h*w).
+ * cam_raw (B, T', h, w) = ReLU(sum_c alpha * act); out (B, OH, OW) = per-clip min-max normalised mean over frames of the
+ * bilinear resize (align_corners = False) of every frame.  Deviation: a constant map (reference: 0/0 = NaN) becomes zeros.
+ * act_rows_per_clip must equal T'*h*w, and T'*h*w <= 16384. */
+int md_gradcam(const float* act, int32_t act_rows_per_clip, int32_t C, int32_t Cpad, int32_t Tq, int32_t h, int32_t w,
+               const float* dfeat, int32_t B, int32_t OH, int32_t OW, float* cam_raw, float* out, void* stream);
+/* Head-fused attention probabilities (visualize_attention.py:47-55 then :78-84): out (B, S, S) = fuse over the H heads of
+ * softmax(q_h k_h^T * d_head^-0.5), the fp32 products summed in fp64; fusion 0 = mean, 1 = max, 2 = min.  qkv as md_attention_fwd
+ * (batch_first 0: [S][B][3D], 1: [B][S][3D]), 16-byte aligned, d_head = D / H a multiple of 4, 32 d_head + 96 S <= 65536. */
+int md_attention_probs_fused(const float* qkv, int32_t S, int32_t B, int32_t D, int32_t H, int32_t batch_first, int32_t fusion,
+                             float* out, void* stream);
+/* Discard (visualize_attention.py:86-90, :122-126): fused_out = fused (B_clips * n_seq_per_clip maps of S x S), then the union
+ * over a clip's sequences of the flat indices of each sequence's k smallest entries, index 0 excepted, is zeroed in the FIRST
+ * sequence of that clip only (the reference's `flat[0, indices] = 0`).  Exactly k entries per sequence: all below the k-th
+ * smallest value, then ties at that value in ascending flat index order.  fused and fused_out must not overlap. */
+int md_rollout_discard(const float* fused, int32_t n_seq_per_clip, int32_t B_clips, int32_t S, int32_t k, float* fused_out,
+                       void* stream);
+/* Rollout chain (visualize_attention.py:71-99, :109-127): result (n_seq, S, S) = prod_l (A_l + I) / 2 with the newest layer on the
+ * left (torch.bmm(a, result)); fused_layers (L, n_seq, S, S).  Exact fp32 FMA; S <= 1024. */
+int md_rollout_chain(const float* fused_layers, int32_t L, int32_t n_seq, int32_t S, float* result, void* stream);
+/* Rollout mask divided by the clip's maximum: kind 0 (space, :101-104) out (B_clips, n_seq_per_clip, S-1) = result[:, 0, 1:];
+ * kind 1 (temporal, :132-134) out (B_clips, n_seq_per_clip, S-1, S-1) = result[:, 1:, 1:]. */
+int md_rollout_mask(const float* result, int32_t B_clips, int32_t n_seq_per_clip, int32_t S, int32_t kind, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
