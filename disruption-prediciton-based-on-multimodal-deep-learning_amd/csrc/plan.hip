@@ -8,6 +8,7 @@
 //   * block outputs z = leaky(skip + main) are materialised (two consumers each);
 //   * backward keeps 4 gradient scratch buffers and runs BN-backward in place.
 #include <vector>
+#include <unordered_map>
 #include <cstdlib>
 #include <new>
 #include "common.h"
@@ -15,6 +16,8 @@
 extern "C" int md_bn_bwd_apply_fused(const float* dA, int g_in, const MdActView* main, const MdActView* skip, float alpha,
                                      const float* mean, const float* invstd, const float* partial, int32_t blocks, int64_t count,
                                      float* dgamma, float* dbeta, int64_t rows, int32_t C, float* d_raw, float* dS, void* stream);
+extern "C" int md_stem_dgrad_supported(const MdConvDesc* d);
+extern "C" int md_stem_dgrad(const MdConvDesc* d, const float* dy_raw, const float* w, float* dx, void* stream);
 extern "C" int md_bn_eval_params(int32_t C, const float* gamma, const float* beta, const float* rmean, const float* rvar,
                                  float eps, float* mean, float* invstd, float* scale, float* shift, void* stream);
 
@@ -80,6 +83,8 @@ struct MdPlan {
   // measured 32 reductions of 6-10 us, each behind a dependent-launch gap, on the critical chain of the one-stream schedule)
   std::vector<WgradPending> pending;
   bool batch_reduce = true;
+  // mode of the last md_plan_forward into each workspace (1 training, 0 eval): md_plan_input_grad refuses a training workspace
+  std::unordered_map<const void*, int> fwd_mode;
 };
 
 // Round 3: the default schedule is ONE stream.  With two workgroups per CU the weight-gradient kernels fill the chip on their own,
@@ -406,6 +411,7 @@ extern "C" int md_plan_forward(MdPlan* P, const float* x, const float* const* w,
   if (!P || !x || !w || !gamma || !beta || !feat || !workspace) return MD_ERR_NULL;
   if (!training && (!rmean || !rvar)) return MD_ERR_NULL;
   float* ws = (float*)workspace;
+  P->fwd_mode[workspace] = training ? 1 : 0;
   RC(md_nchw_to_cl(x, P->B, 3, (int64_t)P->T * P->H * P->W, ws + P->z[0].off, stream));
   // pack every GEMM operand up front: one batched launch for the patch-format ones, per-unit for the rest
   {
@@ -705,6 +711,105 @@ extern "C" int md_plan_backward(MdPlan* P, const float* dfeat, const float* cons
   WgradBeside beside_hint;
 
   return md_plan_backward_range(P, dfeat, w, gamma, dw, dgamma, dbeta, workspace, 4, 0, stream);
+}
+
+// Eval-mode backward of the whole plan (see the header).  The chain mirrors block_backward / md_plan_backward_range with the same
+// four gradient buffers, but a unit costs ONE streaming pass (md_bn_eval_bwd, or md_residual_eval_bwd at a block close, which also
+// forms the d_raw of a downsampling skip unit) and ONE data gradient: no reduction, no finalize, no weight gradient.  Nothing of
+// the training backward's state (bwd_p, red_blocks, pending reductions, side stream) is read or written.
+extern "C" int md_plan_input_grad(MdPlan* P, const float* dfeat, const float* const* w, void* workspace, int32_t stop_z, float* dz_out,
+                                  float* dx, void* stream) {
+  if (!P || !dfeat || !w || !workspace) return MD_ERR_NULL;
+  const int nz = (int)P->z.size();
+  if (stop_z >= nz) return MD_ERR_BAD_SHAPE;
+  if (stop_z >= 0 && !dz_out) return MD_ERR_NULL;
+  if (stop_z < 0 && !dx) return MD_ERR_NULL;
+  {
+    auto it = P->fwd_mode.find(workspace);
+    if (it != P->fwd_mode.end() && it->second != 0) return MD_ERR_UNSUPPORTED;      // holds a training forward
+  }
+  float* ws = (float*)workspace;
+  hipStream_t hs = (hipStream_t)stream;
+  const int low_z = dx ? 0 : stop_z;                 // the chain runs down to this materialised tensor
+  const int n = (int)P->units.size();
+  std::vector<unsigned char> need(n, 0);             // units the chain walks
+  if (low_z <= 0) need[0] = need[1] = 1;             // the stem's two units lie between z[0] and z[1]
+  for (const Block& b : P->blocks)
+    if (b.out_z > low_z)
+      for (int ui : {b.c1s, b.c1t, b.c2s, b.c2t, b.dss, b.dst}) if (ui >= 0) need[ui] = 1;
+  const bool stem_direct = md_stem_dgrad_supported(&P->units[0].d) != 0;
+  {   // data-gradient operands (an eval forward packs none)
+    std::vector<const MdConvDesc*> descs(n); std::vector<int> dg(n, 1);
+    std::vector<const float*> wsrc(n); std::vector<float*> outs(n); std::vector<unsigned char> handled(n);
+    for (int i = 0; i < n; ++i) {
+      const Unit& u = P->units[i];
+      if (!w[i]) return MD_ERR_NULL;
+      descs[i] = &u.d; wsrc[i] = w[i];
+      outs[i] = (need[i] && !(i == 0 && stem_direct)) ? ws + u.wd_off : nullptr;
+    }
+    RC(patch_pack_batch(n, descs.data(), dg.data(), wsrc.data(), outs.data(), handled.data(), hs));
+    for (int i = 0; i < n; ++i)
+      if (!handled[i] && outs[i]) RC(md_conv_pack_weights(&P->units[i].d, w[i], nullptr, outs[i], stream));
+  }
+  auto G = [&](int b) { return ws + P->g_off[b]; };
+  auto copy_out = [&](int zi, const float* src) -> int {
+    if (zi != stop_z) return MD_OK;
+    const size_t bytes = (size_t)P->z[zi].rows * md_cpad(P->z[zi].C) * 4;
+    return hipMemcpyAsync(dz_out, src, bytes, hipMemcpyDeviceToDevice, hs) == hipSuccess ? MD_OK : MD_ERR_LAUNCH;
+  };
+  // G[gb] holds dA of unit ui -> d_raw in place -> data gradient into G[dxb]
+  auto unit_eval_bwd = [&](int ui, int gb, int dxb, int accumulate, bool raw_done) -> int {
+    const Unit& u = P->units[ui];
+    if (!raw_done) {
+      MdActView v = unit_out_view(P, ws, ui);
+      RC(md_bn_eval_bwd(G(gb), &v, u.rows, u.d.Cout, G(gb), stream));
+    }
+    return md_conv_dgrad(&u.d, G(gb), ws + u.wd_off, G(dxb), accumulate, stream);
+  };
+  int p = 0;
+  const ZT& zl = P->z.back();
+  RC(md_avgpool_bwd(dfeat, P->B, zl.C, zl.rows / P->B, G(p), stream));
+  for (int bi = (int)P->blocks.size() - 1; bi >= 0; --bi) {
+    const Block& b = P->blocks[bi];
+    RC(copy_out(b.out_z, G(p)));
+    if (b.out_z <= low_z) return MD_OK;
+    int fr[3], k = 0;
+    for (int i = 0; i < 4; ++i) if (i != p) fr[k++] = i;
+    const int a = fr[0], bb = fr[1], c = fr[2];
+    const Unit& t2 = P->units[b.c2t];
+    MdActView mainv = unit_out_view(P, ws, b.c2t);
+    if (b.dst >= 0) {
+      MdActView skipv = unit_out_view(P, ws, b.dst);
+      RC(md_residual_eval_bwd(G(p), ws + P->z[b.out_z].off, &mainv, &skipv, P->alpha, t2.rows, t2.d.Cout, G(a), G(p), 0, stream));
+    } else {
+      RC(md_residual_eval_bwd(G(p), ws + P->z[b.out_z].off, &mainv, nullptr, P->alpha, t2.rows, t2.d.Cout, G(a), G(p), 0, stream));
+    }
+    RC(unit_eval_bwd(b.c2t, a, bb, 0, true));
+    RC(unit_eval_bwd(b.c2s, bb, a, 0, false));
+    RC(unit_eval_bwd(b.c1t, a, bb, 0, false));
+    if (b.dst < 0) {
+      RC(unit_eval_bwd(b.c1s, bb, p, 1, false));        // dX accumulates onto the identity skip's gradient
+    } else {
+      RC(unit_eval_bwd(b.c1s, bb, c, 0, false));
+      RC(unit_eval_bwd(b.dst, p, a, 0, true));          // G[p] is already the skip unit's d_raw
+      RC(unit_eval_bwd(b.dss, a, c, 1, false));
+      p = c;
+    }
+  }
+  RC(copy_out(1, G(p)));
+  if (low_z >= 1) return MD_OK;
+  const int q = (p + 1) & 3, r = (p + 2) & 3;
+  RC(unit_eval_bwd(1, p, q, 0, false));
+  {
+    const Unit& u0 = P->units[0];
+    MdActView v = unit_out_view(P, ws, 0);
+    RC(md_bn_eval_bwd(G(q), &v, u0.rows, u0.d.Cout, G(q), stream));
+    if (stem_direct) RC(md_stem_dgrad(&u0.d, G(q), w[0], G(r), stream));
+    else RC(md_conv_dgrad(&u0.d, G(q), ws + u0.wd_off, G(r), 0, stream));
+  }
+  RC(copy_out(0, G(r)));
+  if (dx) RC(md_cl_to_nchw(G(r), P->B, 3, (int64_t)P->T * P->H * P->W, dx, stream));
+  return MD_OK;
 }
 
 extern "C" int md_version(const char** arch_out) {

@@ -29,12 +29,13 @@ __global__ __launch_bounds__(256) void k_head_eval_dfeat(const float* __restrict
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          const float* __restrict__ rmean, const float* __restrict__ rvar, float eps,
                                                          float alpha, const float* __restrict__ w1, const int64_t* __restrict__ target,
-                                                         float* __restrict__ dfeat) {
+                                                         const float* __restrict__ dlogits, float* __restrict__ dfeat) {
   extern __shared__ float sm[];
   float* fs = sm;        // [D]
   float* g = sm + D;     // [Hd]
   const int b = blockIdx.x, t = threadIdx.x, nt = blockDim.x;
-  const int64_t tg = target[b];
+  // target != nullptr: the one-hot gradient of md_head_eval_dfeat; otherwise an arbitrary dlogits row (md_head_eval_bwd)
+  const int64_t tg = target ? target[b] : 0;
   const bool ok = tg >= 0 && tg < K;
   for (int d = t; d < D; d += nt) fs[d] = feat[(size_t)b * D + d];
   __syncthreads();
@@ -44,7 +45,14 @@ __global__ __launch_bounds__(256) void k_head_eval_dfeat(const float* __restrict
     const float is = 1.f / sqrtf(rvar[j] + eps);
     const float y = (a - rmean[j]) * is * gamma[j] + beta[j];
     const float da = y > 0.f ? 1.f : (alpha >= 0.f ? alpha * expf(y) : -alpha);     // ELU'(y) | LeakyReLU'(y), as md_head_fwd
-    g[j] = ok ? w1[(size_t)tg * Hd + j] * da * gamma[j] * is : __builtin_nanf("");
+    float up;
+    if (target) {
+      up = ok ? w1[(size_t)tg * Hd + j] : __builtin_nanf("");
+    } else {
+      up = 0.f;
+      for (int k = 0; k < K; ++k) up = fmaf(dlogits[(size_t)b * K + k], w1[(size_t)k * Hd + j], up);
+    }
+    g[j] = up * da * gamma[j] * is;
   }
   __syncthreads();
   for (int d = t; d < D; d += nt) {
@@ -62,7 +70,20 @@ extern "C" int md_head_eval_dfeat(const float* feat, int32_t B, int32_t D, int32
   const size_t lds = (size_t)(D + Hd) * 4;
   if (lds > 65536) return MD_ERR_UNSUPPORTED;
   MD_KLAUNCH(k_head_eval_dfeat, dim3(B), dim3(256), lds, (hipStream_t)stream, feat, D, Hd, K, w0, b0, gamma, beta, rmean, rvar, eps,
-             elu_alpha, w1, target, dfeat);
+             elu_alpha, w1, target, (const float*)nullptr, dfeat);
+  MD_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+extern "C" int md_head_eval_bwd(const float* dlogits, const float* feat, int32_t B, int32_t D, int32_t Hd, int32_t K, const float* w0,
+                                const float* b0, const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
+                                float elu_alpha, const float* w1, float* dfeat, void* stream) {
+  if (!dlogits || !feat || !w0 || !b0 || !gamma || !beta || !rmean || !rvar || !w1 || !dfeat) return MD_ERR_NULL;
+  if (B <= 0 || D <= 0 || Hd <= 0 || K <= 0 || !(eps >= 0.f)) return MD_ERR_BAD_SHAPE;
+  const size_t lds = (size_t)(D + Hd) * 4;
+  if (lds > 65536) return MD_ERR_UNSUPPORTED;
+  MD_KLAUNCH(k_head_eval_dfeat, dim3(B), dim3(256), lds, (hipStream_t)stream, feat, D, Hd, K, w0, b0, gamma, beta, rmean, rvar, eps,
+             elu_alpha, w1, (const int64_t*)nullptr, dlogits, dfeat);
   MD_CHECK_LAUNCH();
   return MD_OK;
 }
@@ -101,13 +122,17 @@ static __device__ __forceinline__ float gradcam_sample(const float* cs, int Tq, 
 }
 
 __global__ __launch_bounds__(512) void k_gradcam_map(const float* __restrict__ cam_raw, int Tq, int h, int w, int OH, int OW, float sh,
-                                                     float sw, float* __restrict__ out) {
-  extern __shared__ float cs[];     // [Tq][h][w] of this clip
+                                                     float sw, int use_lds, float* __restrict__ out) {
+  extern __shared__ float cs_lds[];     // [Tq][h][w] of this clip (use_lds), else the clip is sampled from memory
   __shared__ float wmn[8], wmx[8];
   const int b = blockIdx.x, t = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
   const int n = Tq * h * w, np = OH * OW;
-  for (int e = t; e < n; e += nt) cs[e] = cam_raw[(size_t)b * n + e];
-  __syncthreads();
+  const float* cs = cam_raw + (size_t)b * n;
+  if (use_lds) {
+    for (int e = t; e < n; e += nt) cs_lds[e] = cam_raw[(size_t)b * n + e];
+    __syncthreads();
+    cs = cs_lds;
+  }
   float mn = INFINITY, mx = -INFINITY;
   for (int p = t; p < np; p += nt) {
     const float v = gradcam_sample(cs, Tq, h, w, OW, sh, sw, p);
@@ -140,7 +165,71 @@ extern "C" int md_gradcam(const float* act, int32_t act_rows_per_clip, int32_t C
              (float)act_rows_per_clip, cam_raw);
   MD_CHECK_LAUNCH();
   MD_KLAUNCH(k_gradcam_map, dim3(B), dim3(512), lds, s, (const float*)cam_raw, Tq, h, w, OH, OW, (float)h / (float)OH,
-             (float)w / (float)OW, out);
+             (float)w / (float)OW, 1, out);
+  MD_CHECK_LAUNCH();
+  return MD_OK;
+}
+
+// Grad-CAM at a layer where the gradient is not uniform (visualize_cam.py:87-103 as written: alpha = mean over (T', h, w) of the
+// gradient).  Launch 1: GC_SLICES workgroups per clip sum their rows of dact per channel; launch 2: one workgroup per clip adds the
+// slices in ascending order and divides by T'*h*w; then k_gradcam_raw (with thw = 1: the weights are means already) and
+// k_gradcam_map exactly as md_gradcam.  A layer whose (T', h, w) does not fit the LDS is sampled from memory instead.
+constexpr int GC_SLICES = 32;
+
+__global__ __launch_bounds__(256) void k_gradcam_wsum(const float* __restrict__ dact, int64_t rpc, int C4, float* __restrict__ part) {
+  __shared__ float4 red[256];
+  const int b = blockIdx.y, sl = blockIdx.x;
+  const int nr = blockDim.x / C4, c4 = threadIdx.x % C4, r = threadIdx.x / C4;
+  const int64_t per = (rpc + GC_SLICES - 1) / GC_SLICES;
+  const int64_t beg = (int64_t)sl * per, end = beg + per < rpc ? beg + per : rpc;
+  const float* xb = dact + (size_t)b * rpc * C4 * 4;
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (r < nr)
+    for (int64_t row = beg + r; row < end; row += nr) {
+      const float4 v = *(const float4*)(xb + ((size_t)row * C4 + c4) * 4);
+      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+  red[threadIdx.x] = a;
+  __syncthreads();
+  if (r == 0) {
+    float4 s = red[c4];
+    for (int q = 1; q < nr; ++q) { const float4 v = red[q * C4 + c4]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+    *(float4*)(part + (((size_t)b * GC_SLICES + sl) * C4 + c4) * 4) = s;
+  }
+}
+__global__ __launch_bounds__(256) void k_gradcam_wfin(const float* __restrict__ part, int C, int Cp, float thw, float* __restrict__ wts) {
+  const int b = blockIdx.x;
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float s = 0.f;
+    for (int i = 0; i < GC_SLICES; ++i) s += part[((size_t)b * GC_SLICES + i) * Cp + c];
+    wts[(size_t)b * C + c] = s / thw;
+  }
+}
+
+extern "C" size_t md_gradcam_grad_scratch_floats(int32_t B, int32_t C) {
+  return (B > 0 && C > 0) ? (size_t)B * GC_SLICES * md_cpad(C) : 0;
+}
+
+extern "C" int md_gradcam_grad(const float* act, const float* dact, int32_t B, int32_t Tq, int32_t h, int32_t w, int32_t C, int32_t OH,
+                               int32_t OW, float* weights, float* cam_raw, float* out, float* scratch, void* stream) {
+  if (!act || !dact || !weights || !cam_raw || !out || !scratch) return MD_ERR_NULL;
+  if (B <= 0 || B > 65535 || C <= 0 || Tq <= 0 || h <= 0 || w <= 0 || OH <= 0 || OW <= 0) return MD_ERR_BAD_SHAPE;
+  const int Cp = md_cpad(C), C4 = Cp / 4;
+  if (C4 > 256) return MD_ERR_UNSUPPORTED;
+  const int64_t rpc = (int64_t)Tq * h * w;
+  if (rpc > 0x7fffffff || (int64_t)OH * OW > (1LL << 30)) return MD_ERR_BAD_SHAPE;
+  const int64_t rows = (int64_t)B * rpc;
+  hipStream_t s = (hipStream_t)stream;
+  MD_KLAUNCH(k_gradcam_wsum, dim3(GC_SLICES, B), dim3(256), 0, s, dact, rpc, C4, scratch);
+  MD_CHECK_LAUNCH();
+  MD_KLAUNCH(k_gradcam_wfin, dim3(B), dim3(256), 0, s, (const float*)scratch, C, Cp, (float)rpc, weights);
+  MD_CHECK_LAUNCH();
+  MD_KLAUNCH(k_gradcam_raw, dim3((unsigned)md_cdiv64(rows, 4)), dim3(256), 0, s, act, rows, (int)rpc, C, Cp, (const float*)weights, 1.f,
+             cam_raw);
+  MD_CHECK_LAUNCH();
+  const int use_lds = (size_t)rpc * 4 <= 65536 ? 1 : 0;
+  MD_KLAUNCH(k_gradcam_map, dim3(B), dim3(512), use_lds ? (size_t)rpc * 4 : 0, s, (const float*)cam_raw, Tq, h, w, OH, OW,
+             (float)h / (float)OH, (float)w / (float)OW, use_lds, out);
   MD_CHECK_LAUNCH();
   return MD_OK;
 }

@@ -178,6 +178,16 @@ SIGNATURES = {
     "md_rollout_discard": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "md_rollout_chain": (C.c_int, [_P, _I32, _I32, _I32, _P, _P]),
     "md_rollout_mask": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
+    "md_bn_eval_bwd": (C.c_int, [_P, _VIEW, _I64, _I32, _P, _P]),
+    "md_residual_eval_bwd": (C.c_int, [_P, _P, _VIEW, _VIEW, _F, _I64, _I32, _P, _P, C.c_int, _P]),
+    "md_stem_dgrad_supported": (C.c_int, [_DESC]),
+    "md_stem_dgrad": (C.c_int, [_DESC, _P, _P, _P, _P]),
+    "md_plan_input_grad": (C.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P]),
+    "md_head_eval_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P]),
+    "md_gradcam_grad_scratch_floats": (_SZ, [_I32, _I32]),
+    "md_gradcam_grad": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "md_saliency_scratch_floats": (_SZ, [_I32]),
+    "md_saliency_map": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
 }
 
 ERRORS = {-1: "bad shape", -2: "unsupported", -3: "workspace", -4: "kernel launch failed", -5: "null pointer"}

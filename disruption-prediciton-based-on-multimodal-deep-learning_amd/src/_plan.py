@@ -120,6 +120,23 @@ class TrunkPlan:
                                                _ptr_array(dbetas), ws.data_ptr(), hi, lo, _stream()),
                 "md_plan_backward_range")
 
+    def input_grad(self, dfeat, ws, weights, want_dx: bool = True, stop_z: int = -1):
+        """Eval-mode backward (md_plan_input_grad) through the eval forward that ``ws`` holds: returns (dx (B,3,T,H,W) or None,
+        dz [rows, cpad(C)] at materialised tensor ``stop_z`` or None).  With ``want_dx`` False the chain stops at ``stop_z``."""
+        B, T, H, W = self.shape
+        dfeat = dfeat.contiguous()
+        require_cuda(dfeat, ws)
+        dx = torch.empty((B, 3, T, H, W), device=dfeat.device, dtype=torch.float32) if want_dx else None
+        dz = None
+        if stop_z >= 0:
+            off, rows, cc = C.c_size_t(), C.c_int64(), C.c_int32()
+            N.check(N.lib().md_plan_z_layout(self._h, stop_z, C.byref(off), C.byref(rows), C.byref(cc)), "md_plan_z_layout")
+            dz = torch.empty((rows.value, (cc.value + 3) & ~3), device=dfeat.device, dtype=torch.float32)
+        N.check(N.lib().md_plan_input_grad(self._h, dfeat.data_ptr(), _ptr_array(weights), ws.data_ptr(), int(stop_z),
+                                           None if dz is None else dz.data_ptr(), None if dx is None else dx.data_ptr(),
+                                           _stream()), "md_plan_input_grad")
+        return dx, dz
+
 
 class TrunkFunction(torch.autograd.Function):
     """feat = R2Plus1DNet(x); parameters are passed flat as [w_0.., gamma_0.., beta_0..]."""
@@ -143,14 +160,19 @@ class TrunkFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dfeat):
-        if not ctx.training:
-            raise RuntimeError("R2Plus1DNet: backward through an eval-mode forward is not supported on the MI355X path "
-                               "(BatchNorm uses running statistics there; call model.train() or wrap the forward in no_grad)")
         if ctx.ws is None:
             raise RuntimeError("R2Plus1DNet: this forward was run without saving activations (no parameter required a gradient)")
         plan: TrunkPlan = ctx.plan
         n = plan.num_units
         params = ctx.params
+        if not ctx.training:
+            # eval mode (running statistics): the input gradient only -- parameters get None
+            if not ctx.needs_input_grad[1]:
+                raise RuntimeError("R2Plus1DNet: backward through an eval-mode forward gives the INPUT gradient only, and the "
+                                   "input does not require one (parameter gradients need model.train())")
+            dx, _ = plan.input_grad(dfeat, ctx.ws, params[:n])
+            ctx.ws = None
+            return (None, dx, None, None, None, None, None) + (None,) * len(params)
         weights, gammas = params[:n], params[n:2 * n]
         dev = dfeat.device
         dfeat = dfeat.contiguous()

@@ -61,6 +61,33 @@ def bump_batches_tracked(bn) -> None:
         bn.num_batches_tracked += 1
 
 
+# Explainability switch (src/visualization/visualize_cam.py::GradCAM_SlowFast), off by default: inside ``capture_units({name:
+# conv weight})`` the eval-mode backward of the unit / plain convolution that owns one of those weights leaves
+# out[name] = (raw convolution output, its gradient), both channels-last [B,T,H,W,Cp] -- what a forward hook and a full backward
+# hook on the reference's Conv3d module see.
+_capture = None
+
+
+class capture_units:
+    def __init__(self, weights):
+        self.keys = {w.data_ptr(): name for name, w in weights.items()}
+        self.out = {}
+
+    def __enter__(self):
+        global _capture
+        self.outer, _capture = _capture, self
+        return self
+
+    def __exit__(self, *exc):
+        global _capture
+        _capture = self.outer
+        return False
+
+
+def _capture_key(w):
+    return (_capture, _capture.keys[w.data_ptr()]) if _capture is not None and w.data_ptr() in _capture.keys else None
+
+
 class ConvBnLeakyFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, gamma, beta, rmean, rvar, stride, padding, slope, training, eps, momentum, cl_channels=0):
@@ -80,7 +107,8 @@ class ConvBnLeakyFunction(torch.autograd.Function):
         d = ops.make_desc(B, T, H, W, Cin, Cout, tuple(w.shape[2:]), tuple(stride), tuple(padding))
         if xcl is None:
             xcl = ops.to_channels_last(x.contiguous().float())
-        wf, wd = ops.pack_weights(d, w.contiguous(), want_dgrad=training)
+        eval_dx = (not training) and ctx.needs_input_grad[0]       # eval mode: only the input gradient exists
+        wf, wd = ops.pack_weights(d, w.contiguous(), want_dgrad=training or eval_dx)
         y, part = ops.conv_fwd(d, ops.view(xcl), wf, x.device, want_stats=training)
         rows = y.numel() // y.shape[-1]
         if training:
@@ -96,14 +124,32 @@ class ConvBnLeakyFunction(torch.autograd.Function):
             ctx.d = d
             ctx.slope = slope
             ctx.save_for_backward(xcl, y, st, wd)
+        elif eval_dx:
+            ctx.d = d
+            ctx.slope = slope
+            ctx.save_for_backward(y, st, wd)
         ctx.training = training
+        ctx.eval_dx = eval_dx
+        ctx.capture = _capture_key(w) if eval_dx else None
         ctx.cl = bool(cl_channels)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         if not ctx.training:
-            raise RuntimeError("mi355x hot path: backward through an eval-mode BatchNorm unit is not supported")
+            if not ctx.eval_dx:
+                raise RuntimeError("mi355x hot path: backward through an eval-mode BatchNorm unit gives the INPUT gradient only, "
+                                   "and its input did not require one (parameter gradients need model.train())")
+            y, st, wd = ctx.saved_tensors
+            d = ctx.d
+            dA = dout.contiguous().float() if ctx.cl else ops.to_channels_last(dout.contiguous().float())
+            d_raw = ops.bn_eval_backward(dA, ops.view(y, st[2], st[3], ctx.slope), d.Cout)
+            if ctx.capture is not None:
+                ctx.capture[0].out[ctx.capture[1]] = (y, d_raw, d.Cout)
+            dx = ops.conv_dgrad(d, d_raw, wd)
+            if not ctx.cl:
+                dx = ops.from_channels_last(dx, d.Cin)
+            return (dx,) + (None,) * 12
         xcl, y, st, wd = ctx.saved_tensors
         d = ctx.d
         dA = dout.contiguous().float() if ctx.cl else ops.to_channels_last(dout.contiguous().float())
@@ -252,6 +298,38 @@ class HeadFunction(torch.autograd.Function):
         return df, dw0, db0, dg, dbt, dw1, db1, None, None, None, None, None, None
 
 
+class HeadEvalFunction(torch.autograd.Function):
+    """The same head in eval mode (running statistics) for a feature tensor that requires a gradient: md_head_fwd's eval branch
+    forward, md_head_eval_bwd backward.  Only the input gradient exists; the parameters get None (head_apply routes here;
+    HeadFunction itself keeps refusing a backward after an eval-mode forward)."""
+
+    @staticmethod
+    def forward(ctx, f, w0, b0, gamma, beta, w1, b1, rmean, rvar, alpha, eps):
+        ops.require_cuda(f, w0, b0, gamma, beta, w1, b1)
+        f = f.contiguous()
+        B, D = f.shape
+        Hd, K = w0.shape[0], w1.shape[0]
+        L = N.lib()
+        logits = torch.empty((B, K), device=f.device, dtype=torch.float32)
+        save = torch.empty(L.md_head_save_floats(B, D, Hd), device=f.device, dtype=torch.float32)
+        N.check(L.md_head_fwd(ops._p(f), B, D, Hd, K, ops._p(w0), ops._p(b0), ops._p(gamma), ops._p(beta), ops._p(w1),
+                              ops._p(b1), alpha, eps, 0.0, 0, ops._p(rmean), ops._p(rvar), ops._p(logits),
+                              ops._p(save), ops._stream()), "md_head_fwd")
+        ctx.save_for_backward(f, w0, b0, gamma, beta, rmean, rvar, w1)
+        ctx.alpha, ctx.eps = alpha, eps
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        f, w0, b0, gamma, beta, rmean, rvar, w1 = ctx.saved_tensors
+        B, D = f.shape
+        df = torch.empty_like(f)
+        N.check(N.lib().md_head_eval_bwd(ops._p(dlogits.contiguous().float()), ops._p(f), B, D, w0.shape[0], w1.shape[0], ops._p(w0),
+                                         ops._p(b0), ops._p(gamma), ops._p(beta), ops._p(rmean), ops._p(rvar), ctx.eps, ctx.alpha,
+                                         ops._p(w1), ops._p(df), ops._stream()), "md_head_eval_bwd")
+        return (df,) + (None,) * 10
+
+
 class ConvFunction(torch.autograd.Function):
     """Plain Conv3d (no bias, no normalisation): the SlowFast laterals (reference slowfast.py:58-65)."""
 
@@ -272,6 +350,8 @@ class ConvFunction(torch.autograd.Function):
         y, _ = ops.conv_fwd(d, ops.view(xcl), wf, x.device, want_stats=False)
         ctx.d = d
         ctx.cl = bool(cl_channels)
+        ctx.capture = _capture_key(w)
+        ctx.cap_y = y.detach() if ctx.capture is not None else None
         ctx.save_for_backward(xcl, wd)
         return y if cl_channels else ops.from_channels_last(y, Cout)
 
@@ -280,6 +360,8 @@ class ConvFunction(torch.autograd.Function):
         xcl, wd = ctx.saved_tensors
         d = ctx.d
         dy = dout.contiguous().float() if ctx.cl else ops.to_channels_last(dout.contiguous().float())
+        if ctx.capture is not None:
+            ctx.capture[0].out[ctx.capture[1]] = (ctx.cap_y, dy, d.Cout)
         dx = None
         if ctx.needs_input_grad[0] and streams.unit_helpers(dy):
             with streams.fork(dy.device, None, (dy, xcl)) as f:            # weight gradient beside the data gradient
@@ -1112,6 +1194,9 @@ def head_apply(f, lin0: torch.nn.Linear, bn: torch.nn.BatchNorm1d, lin1: torch.n
     import os
     fused_max = int(os.environ.get("MD_HEAD_FUSED_MAX", "65536"))
     if 2 * B * Hd * 4 <= 60000 and lin0.in_features * Hd <= fused_max:
+        if not training and torch.is_grad_enabled() and f.requires_grad:       # eval mode, differentiated with respect to the input
+            return HeadEvalFunction.apply(f, lin0.weight, lin0.bias, bn.weight, bn.bias, lin1.weight, lin1.bias, bn.running_mean,
+                                          bn.running_var, float(alpha), float(bn.eps))
         out = HeadFunction.apply(f, lin0.weight, lin0.bias, bn.weight, bn.bias, lin1.weight, lin1.bias, bn.running_mean, bn.running_var,
                                  float(alpha), float(bn.eps), float(bn.momentum), bool(training))
         if training:

@@ -265,6 +265,15 @@ def conv_dgrad(d: N.MdConvDesc, dy: torch.Tensor, wd: torch.Tensor, out: Optiona
     return out
 
 
+def bn_eval_backward(dA: torch.Tensor, y: N.MdActView, Cc: int, inplace: bool = False) -> torch.Tensor:
+    """d_raw of an eval-mode BatchNorm + LeakyReLU unit (md_bn_eval_bwd): dA * leaky'(scale * y + shift) * scale."""
+    require_cuda(dA); f32(dA)
+    rows = dA.numel() // dA.shape[-1]
+    out = dA if inplace else torch.empty_like(dA)
+    N.check(N.lib().md_bn_eval_bwd(_p(dA), C.byref(y), rows, Cc, _p(out), _stream()), "md_bn_eval_bwd")
+    return out
+
+
 def conv_dgrad_bnred(d: N.MdConvDesc, dy: torch.Tensor, wd: torch.Tensor, y_view: N.MdActView, st: torch.Tensor,
                      out: Optional[torch.Tensor] = None, accumulate: bool = False):
     """Data gradient with the BatchNorm-backward reduction of the producing unit fused into the epilogue

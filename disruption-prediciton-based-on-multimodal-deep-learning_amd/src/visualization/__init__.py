@@ -1,5 +1,6 @@
-"""Explainability tools of the reference's ``src/visualization`` on the MI355X: ``visualize_cam.GradCAM_R2Plus1D`` and
-``visualize_attention.ViViTAttentionRollout`` (maps computed by the gfx950 kernels of csrc/xai.hip, batched over clips)."""
+"""Explainability tools of the reference's ``src/visualization`` on the MI355X: ``visualize_cam.GradCAM_R2Plus1D`` /
+``GradCAM_SlowFast``, ``visualize_attention.ViViTAttentionRollout`` and ``visualize_saliency.InputGradient`` (maps computed by the
+gfx950 kernels of csrc/xai.hip and csrc/eval_bwd.hip, batched over clips)."""
 import os as _os
 
 _ref = _os.environ.get("MD_REFERENCE_SRC")

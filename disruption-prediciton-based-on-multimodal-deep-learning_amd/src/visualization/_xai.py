@@ -46,6 +46,54 @@ def gradcam(act: torch.Tensor, C: int, Tq: int, h: int, w: int, dfeat: torch.Ten
     return cam_raw, out
 
 
+def head_eval_bwd(feat: torch.Tensor, lin0, bn, lin1, alpha: float, dlogits: torch.Tensor) -> torch.Tensor:
+    """Eval-mode input gradient of the head for an arbitrary dlogits (B, K) (md_head_eval_bwd)."""
+    feat = ops.f32(feat).contiguous()
+    dlogits = ops.f32(dlogits).contiguous()
+    B, D = feat.shape
+    ws = [lin0.weight, lin0.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, lin1.weight]
+    ops.require_cuda(feat, dlogits, *ws)
+    if tuple(dlogits.shape) != (B, lin1.out_features):
+        raise ValueError("dlogits %s for logits (%d, %d)" % (tuple(dlogits.shape), B, lin1.out_features))
+    dfeat = torch.empty_like(feat)
+    N.check(N.lib().md_head_eval_bwd(_p(dlogits), _p(feat), B, D, lin0.out_features, lin1.out_features, *[_p(w) for w in ws[:6]],
+                                     float(bn.eps), float(alpha), _p(lin1.weight), _p(dfeat), _stream()), "md_head_eval_bwd")
+    return dfeat
+
+
+def gradcam_grad(act: torch.Tensor, dact: torch.Tensor, C: int, B: int, Tq: int, h: int, w: int, OH: int, OW: int):
+    """act, dact [B*Tq*h*w, cpad(C)] channels-last -> (weights (B, C), cam_raw (B, Tq, h, w), map (B, OH, OW)) (md_gradcam_grad)."""
+    ops.require_cuda(act, dact)
+    rows = B * Tq * h * w
+    if act.shape[0] != rows or tuple(dact.shape) != tuple(act.shape) or act.shape[1] != ops.cpad(C):
+        raise ValueError("activation %s / gradient %s for B*T'*h*w = %d rows of %d channels" % (tuple(act.shape), tuple(dact.shape), rows, C))
+    L = N.lib()
+    wts = torch.empty((B, C), device=act.device)
+    cam_raw = torch.empty((B, Tq, h, w), device=act.device)
+    out = torch.empty((B, OH, OW), device=act.device)
+    scratch = torch.empty(L.md_gradcam_grad_scratch_floats(B, C), device=act.device)
+    N.check(L.md_gradcam_grad(_p(ops.f32(act)), _p(ops.f32(dact)), B, Tq, h, w, C, OH, OW, _p(wts), _p(cam_raw), _p(out), _p(scratch),
+                              _stream()), "md_gradcam_grad")
+    return wts, cam_raw, out
+
+
+SALIENCY_MODE = {"max": 0, "sum": 1}
+
+
+def saliency_map(dx: torch.Tensor, mode: str = "max") -> torch.Tensor:
+    """dx (B, C, T, H, W) -> (B, T, H, W) in [0, 1]: max | sum over channels of |dx|, per-clip min-max (md_saliency_map)."""
+    if mode not in SALIENCY_MODE:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(SALIENCY_MODE), mode))
+    dx = ops.f32(dx).contiguous()
+    ops.require_cuda(dx)
+    B, Cc, T, H, W = dx.shape
+    L = N.lib()
+    maps = torch.empty((B, T, H, W), device=dx.device)
+    scratch = torch.empty(L.md_saliency_scratch_floats(B), device=dx.device)
+    N.check(L.md_saliency_map(_p(dx), B, Cc, T, H, W, SALIENCY_MODE[mode], _p(maps), _p(scratch), _stream()), "md_saliency_map")
+    return maps
+
+
 def attention_probs_fused(qkv: torch.Tensor, heads: int, fusion: str, batch_first: bool = True, out=None) -> torch.Tensor:
     """(B, S, S) head-fused softmax(q k^T / sqrt(d_head)) of a qkv projection (md_attention_probs_fused)."""
     if fusion not in FUSION:

@@ -590,6 +590,58 @@ int md_rollout_chain(const float* fused_layers, int32_t L, int32_t n_seq, int32_
  * kind 1 (temporal, :132-134) out (B_clips, n_seq_per_clip, S-1, S-1) = result[:, 1:, 1:]. */
 int md_rollout_mask(const float* result, int32_t B_clips, int32_t n_seq_per_clip, int32_t S, int32_t kind, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Eval-mode backward (csrc/eval_bwd.hip, csrc/plan.hip, csrc/xai.hip): what `score.backward()` through a model in eval mode
+ * computes in the reference (src/visualization/visualize_cam.py:84-85, :181-184) for the INPUT and the activations; no
+ * parameter gradients are produced (deviation: the reference also fills every parameter's .grad).
+ * ---------------------------------------------------------------------------------------------- */
+/* BatchNorm3d with running statistics + LeakyReLU (R2Plus1D.py:53-58 in eval mode), backward: with the folded constants of
+ * md_bn_eval_params in y_view,  d_raw[r][c] = dA[r][c] * (p > 0 ? 1 : slope) * scale[c],  p = fmaf(scale[c], y[r][c], shift[c])
+ * exactly as the forward kernels evaluate it.  Channels-last [rows][md_cpad(C)], pad channels written as zeros; d_raw may be dA.
+ * A view without scale / shift passes dA through. */
+int md_bn_eval_bwd(const float* dA, const MdActView* y_view, int64_t rows, int32_t C, float* d_raw, void* stream);
+/* Backward of the block close z = leaky(a_skip + a_main, alpha) (R2Plus1D.py:183-187) in eval mode, a_* = leaky(bn(raw)) of a
+ * unit's view or a plain tensor.  d = dZ * (z > 0 ? 1 : alpha) -- the sign of the sum is the sign of the materialised z;
+ * d_main_raw = d * leaky'(p_main) * scale_main;  dS = d when skip_view is NULL (identity skip: the gradient of the block input's
+ * skip operand) or d * leaky'(p_skip) * scale_skip when it is the downsampling unit's view (then dS is that unit's d_raw).
+ * accumulate_dS != 0 adds into dS.  dS may be dZ; d_main_raw must be a different buffer. */
+int md_residual_eval_bwd(const float* dZ, const float* z, const MdActView* main_view, const MdActView* skip_view, float alpha,
+                         int64_t rows, int32_t C, float* d_main_raw, float* dS, int accumulate_dS, void* stream);
+/* Data gradient of a 1 x kh x kw convolution with at most 4 input channels straight from the weights (Cout,Cin,1,kh,kw): the
+ * R(2+1)D stem (R2Plus1D.py:210: 3 -> 45 channels, 1x7x7, stride 1x2x2), whose data gradient training never needs.  Gather form,
+ * one thread per input pixel, exact fp32 FMA; dx [N*Ti*Hi*Wi][4] channels-last, pad channel zero.  md_stem_dgrad_supported: 1 when
+ * the geometry qualifies (kt = st = 1, pt = 0, Cin <= 4, kh*kw*md_cpad(Cout)*16 bytes <= 64 KiB). */
+int md_stem_dgrad_supported(const MdConvDesc* d);
+int md_stem_dgrad(const MdConvDesc* d, const float* dy_raw, const float* w, float* dx, void* stream);
+/* Eval-mode backward of the whole R2Plus1DNet plan (what autograd does below `score.backward()`, visualize_cam.py:84-85).
+ * `workspace` must hold an EVAL-mode md_plan_forward of this plan with the same weights; a workspace whose last forward through
+ * this plan was a training one is refused with MD_ERR_UNSUPPORTED.  The data-gradient operands are packed here (an eval forward
+ * packs none); then the units are walked in reverse with md_residual_eval_bwd / md_bn_eval_bwd / md_conv_dgrad.
+ *   dx != NULL: runs through the stem and writes d score / d clip as (B,3,T,H,W) fp32.
+ *   stop_z >= 0: the gradient at materialised tensor z[stop_z] (md_plan_z_layout: 0 the clip, 1 the stem output, then one per
+ *   residual block) is copied to dz_out [rows][md_cpad(C)]; with dx == NULL the chain stops there.
+ * No weight / gamma / beta gradient is produced and none of the training backward's state is touched. */
+int md_plan_input_grad(MdPlan* p, const float* dfeat, const float* const* w, void* workspace, int32_t stop_z, float* dz_out,
+                       float* dx, void* stream);
+/* Eval-mode input gradient of the classifier head for an arbitrary dlogits (B, K): md_head_eval_dfeat with
+ * sum_k dlogits[b][k] * W1[k] in place of W1[target]; same device code. */
+int md_head_eval_bwd(const float* dlogits, const float* feat, int32_t B, int32_t D, int32_t Hd, int32_t K, const float* w0,
+                     const float* b0, const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
+                     float elu_alpha, const float* w1, float* dfeat, void* stream);
+/* Grad-CAM (visualize_cam.py:87-103) at a layer where the gradient is not uniform: weights (B, C) = mean over (T', h, w) of dact,
+ * then ReLU / per-frame bilinear resize / time mean / per-clip min-max exactly as md_gradcam (same device code; a constant map
+ * is all zeros).  act, dact [B*T'*h*w][md_cpad(C)] channels-last; cam_raw (B, T', h, w); out (B, OH, OW); scratch:
+ * md_gradcam_grad_scratch_floats(B, C) floats.  Slices of a clip are summed in a fixed order: run-to-run identical. */
+size_t md_gradcam_grad_scratch_floats(int32_t B, int32_t C);
+int md_gradcam_grad(const float* act, const float* dact, int32_t B, int32_t Tq, int32_t h, int32_t w, int32_t C, int32_t OH,
+                    int32_t OW, float* weights, float* cam_raw, float* out, float* scratch, void* stream);
+/* Saliency map of an input gradient dx (B, C, T, H, W) -> maps (B, T, H, W): mode 0 = max over channels of |dx|, 1 = sum over
+ * channels of |dx|; then per-clip min-max to [0, 1] (a constant clip gives zeros).  Two launches, no atomics.
+ * scratch: md_saliency_scratch_floats(B) floats. */
+size_t md_saliency_scratch_floats(int32_t B);
+int md_saliency_map(const float* dx, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t mode, float* maps,
+                    float* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
