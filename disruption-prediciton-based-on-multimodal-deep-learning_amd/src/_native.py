@@ -188,6 +188,20 @@ SIGNATURES = {
     "md_gradcam_grad": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "md_saliency_scratch_floats": (_SZ, [_I32]),
     "md_saliency_map": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "md_sqdist": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "md_tsne_conditional": (C.c_int, [_P, _I32, _F, _P, _P]),
+    "md_tsne_joint_scratch_doubles": (_SZ, [_I32]),
+    "md_tsne_joint": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "md_tsne_rowpart_floats": (_SZ, [_I32, _I32]),
+    "md_tsne_scratch_doubles": (_SZ, [_I32]),
+    "md_tsne_gradient": (C.c_int, [_P, _P, _I32, _I32, _F, _I32, _P, _P, _P, _P, _P]),
+    "md_tsne_update_blocks": (_I32, [_I64]),
+    "md_tsne_update": (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _P]),
+    "md_col_mean_scratch_doubles": (_SZ, [_I64, _I32]),
+    "md_col_mean": (C.c_int, [_P, _I64, _I32, _P, _P, _P]),
+    "md_tsmm_mv": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P]),
+    "md_tsmm_mtw_scratch_doubles": (_SZ, [_I64, _I32, _I32]),
+    "md_tsmm_mtw": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
 }
 
 ERRORS = {-1: "bad shape", -2: "unsupported", -3: "workspace", -4: "kernel launch failed", -5: "null pointer"}

@@ -642,6 +642,49 @@ size_t md_saliency_scratch_floats(int32_t B);
 int md_saliency_map(const float* dx, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W, int32_t mode, float* maps,
                     float* scratch, void* stream);
 
+/* ---- Latent-space maps (csrc/embed.hip): exact t-SNE and the tall-skinny pieces of an incremental PCA.  Every reduction is
+ * fixed-order (partial rows + a second stage, no atomics): two runs on the same input give the same bits.  Dense N x N operands;
+ * N above MD_EMBED_MAX_N is refused with MD_ERR_UNSUPPORTED (32-bit tile indices, 4 GiB per matrix at the limit). */
+#define MD_EMBED_MAX_N 32768
+/* out[N][N] = squared Euclidean distances of x[N][D] in the direct form sum_k (x_ik - x_jk)^2 (no |x|^2 + |y|^2 - 2 x.y
+ * cancellation); symmetric to the bit, diagonal exactly 0. */
+int md_sqdist(const float* x, int32_t N, int32_t D, float* out, void* stream);
+/* Conditional P of t-SNE: per row the bisection of sklearn.manifold._utils._binary_search_perplexity (beta from 1, <= 100 steps,
+ * |H - ln(perplexity)| <= 1e-5, sums in fp64, diagonal excluded and written as 0).  One workgroup per row, the row held in LDS.
+ * p_cond may be d2. */
+int md_tsne_conditional(const float* d2, int32_t N, float perplexity, float* p_cond, void* stream);
+/* Joint P = (C + C^T) / max(sum, eps), off-diagonal clamped to eps = 2.220446e-16, diagonal 0; the total in fp64.  p may be
+ * p_cond.  scratch: md_tsne_joint_scratch_doubles(N) doubles. */
+size_t md_tsne_joint_scratch_doubles(int32_t N);
+int md_tsne_joint(const float* p_cond, int32_t N, float* p, double* scratch, void* stream);
+/* KL gradient of the embedding y[N][nc], nc in {2, 3}, dof = max(nc - 1, 1) (sklearn.manifold._t_sne._kl_divergence term for
+ * term, P taken as exaggeration * p): one pass over p, then grad[N][nc] = c (attractive - repulsive / Z).  stats[0] = Z; with
+ * want_kl also stats[1] = KL(exaggeration * p || Q) and stats[2] = sum of exaggeration * p (Q is not clamped at eps: num / Z
+ * stays far above it for any embedding a descent reaches).  rowpart: md_tsne_rowpart_floats(N, nc) floats; scratch:
+ * md_tsne_scratch_doubles(N) doubles; stats: at least 3 doubles. */
+size_t md_tsne_rowpart_floats(int32_t N, int32_t nc);
+size_t md_tsne_scratch_doubles(int32_t N);
+int md_tsne_gradient(const float* p, const float* y, int32_t N, int32_t nc, float exaggeration, int32_t want_kl, float* rowpart,
+                     double* scratch, float* grad, double* stats, void* stream);
+/* One step of scikit-learn's _gradient_descent over n = N * nc entries: gains += 0.2 where update * grad < 0, else *= 0.8, floor
+ * min_gain; update = momentum * update - lr * gains * grad; y += update.  gpart[md_tsne_update_blocks(n)] receives the
+ * workgroups' shares of |gains * grad|^2 (sum them in index order). */
+int32_t md_tsne_update_blocks(int64_t n);
+int md_tsne_update(float* y, float* update, float* gains, const float* grad, int64_t n, float momentum, float lr, float min_gain,
+                   double* gpart, void* stream);
+/* Column means of x[rows][D] in fp64.  scratch: md_col_mean_scratch_doubles(rows, D) doubles. */
+size_t md_col_mean_scratch_doubles(int64_t rows, int32_t D);
+int md_col_mean(const float* x, int64_t rows, int32_t D, double* mean, double* scratch, void* stream);
+/* Tall-skinny products with the stacked matrix S = [M - mean (rows x D); extra (E x D)] that is never materialised: mean (D floats)
+ * may be NULL (no centring), extra may be NULL when E = 0.  Skinny operands have 8 columns (zero padded), products are fp64 FMAs.
+ *   md_tsmm_mv : W[rows + E][8] = S V,  V[D][8].      (also the projection (X - mean) V)
+ *   md_tsmm_mtw: out[D][8] = S^T W,  W[rows + E][8]; out_f32 and / or out_f64.  scratch: md_tsmm_mtw_scratch_doubles(rows, D, E). */
+int md_tsmm_mv(const float* M, int64_t rows, int32_t D, const float* mean, const float* extra, int32_t E, const float* V, float* W,
+               void* stream);
+size_t md_tsmm_mtw_scratch_doubles(int64_t rows, int32_t D, int32_t E);
+int md_tsmm_mtw(const float* M, int64_t rows, int32_t D, const float* mean, const float* extra, int32_t E, const float* W,
+                float* out_f32, double* out_f64, double* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
