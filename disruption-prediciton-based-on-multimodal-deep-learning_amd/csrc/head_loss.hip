@@ -158,7 +158,8 @@ extern "C" int md_head_bwd(const float* dlogits, const float* feat, int32_t B, i
 // kind 1 LDAM  : z = s*(x - m[y] onehot); L = sum_i w[y_i] nll_i / sum_i w[y_i]   (src/loss.py:58-69)
 // kind 2 CE    : L = sum_i w[y_i] nll_i                                   (src/loss.py:80-81)
 // pred = argmax_k softmax(x) on the UNMODIFIED logits, first maximal index (src/train.py:70).
-#define MAXK 16
+#include "softmax_loss.h"
+#define MAXK MD_LOSS_MAXK
 __global__ __launch_bounds__(256) void k_softmax_loss(int kind, const float* __restrict__ x, const int64_t* __restrict__ y,
                                                       int B, int K, const float* __restrict__ cw,
                                                       const float* __restrict__ margins, float gs,
@@ -170,32 +171,10 @@ __global__ __launch_bounds__(256) void k_softmax_loss(int kind, const float* __r
   for (int b = t; b < B; b += blockDim.x) {
     const int yy = (int)y[b];
     float z[MAXK];
-    float mx = -INFINITY; int arg = 0; float rawmx = -INFINITY;
-    for (int k = 0; k < K; ++k) {
-      float v = x[b * K + k];
-      if (v > rawmx) { rawmx = v; arg = k; }
-      if (kind == 1) { if (k == yy && margins) v -= margins[k]; v *= gs; }
-      z[k] = v; mx = fmaxf(mx, v);
-    }
-    if (pred) pred[b] = arg;
-    float se = 0.f;
-    for (int k = 0; k < K; ++k) se += expf(z[k] - mx);
-    const float lse = mx + logf(se);
-    const float ce = lse - z[yy];
-    const float w = cw ? cw[yy] : 1.f;
-    float coef;   // d L_i / d ce_i
-    if (kind == 0) {
-      const float p = expf(-ce);
-      const float q = 1.f - p;
-      const float qg = powf(q, gs);
-      lsum += (double)(w * qg * ce);
-      float dq = 0.f;
-      if (gs != 0.f && q > 0.f) dq = gs * powf(q, gs - 1.f) * p * ce;
-      coef = w * (qg + dq);
-    } else {
-      lsum += (double)(w * ce);
-      coef = w;
-    }
+    const MdSampleLoss r = md_sample_loss(kind, x + b * K, yy, K, cw, margins, gs, z);   // softmax_loss.h
+    const float lse = r.lse, w = r.w, coef = r.coef;
+    if (pred) pred[b] = r.arg;
+    lsum += (double)r.term;
     wsum += (double)w;
     if (dx) {
       for (int k = 0; k < K; ++k) {

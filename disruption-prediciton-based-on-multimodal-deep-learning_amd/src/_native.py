@@ -202,6 +202,8 @@ SIGNATURES = {
     "md_tsmm_mv": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P]),
     "md_tsmm_mtw_scratch_doubles": (_SZ, [_I64, _I32, _I32]),
     "md_tsmm_mtw": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "md_window_gather": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P]),
+    "md_eval_accumulate": (C.c_int, [_I32, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _F, _P, _I64, _P, _P, _P]),
 }
 
 ERRORS = {-1: "bad shape", -2: "unsupported", -3: "workspace", -4: "kernel launch failed", -5: "null pointer"}

@@ -3,7 +3,11 @@
 Decision rule (:56-58): a sample is labelled 1 ("normal") unless softmax(output)[:, 0] > threshold.  Predictions, labels and
 the loss stay on the GPU until the loop is over (the reference calls ``.item()`` twice per batch); accuracy, macro-F1, ROC-AUC
 and the classification report are then host arithmetic on N integers.  The confusion-matrix / ROC / PR figure is presentation
-and is not drawn (``save_conf`` is accepted and ignored); the text report is written to ``save_txt`` as in the reference."""
+and is not drawn (``save_conf`` is accepted and ignored); the text report is written to ``save_txt`` as in the reference.
+
+``evaluate_detail`` (:242-350) writes the per-sample disruption probability of the train, valid and test loaders to a CSV: softmax
+column 0 goes into one device buffer per loader (``md_eval_accumulate``'s p0 output) and is read back once per loader, where the
+reference synchronises on ``.cpu()`` after every batch."""
 from typing import Literal, Optional
 
 import numpy as np
@@ -93,3 +97,55 @@ def evaluate(test_loader: DataLoader, model: torch.nn.Module, optimizer: Optiona
             f.write("\n# test score : {:.2f}, test loss : {:.3f}, test f1 : {:.3f}, test_auc : {:.3f}".format(
                 test_acc, test_loss, test_f1, test_auc))
     return test_loss, test_acc, test_f1
+
+
+def _loader_probabilities(loader: DataLoader, model: torch.nn.Module, device, model_type: str):
+    """(label, shot, softmax column 0) of every sample of a loader whose dataset yields (data, target, shot_num)."""
+    from . import ops
+    n_total = len(loader.dataset)
+    p0 = torch.zeros(n_total, device=device, dtype=torch.float32)
+    scratch = torch.zeros((1, 1), device=device, dtype=torch.float32)
+    labels, shots, at, segs = [], [], 0, {}
+    for data, target, shot_num in loader:
+        with torch.no_grad():
+            output, _, _ = _forward(model, data, device, model_type)
+            output = output.contiguous().float()
+            n = output.shape[0]
+            if n not in segs:                                  # one upload per batch size (the full one and the ragged last)
+                segs[n] = torch.tensor([0, n], dtype=torch.int32).to(device)
+            seg = segs[n]
+            tgt = target.reshape(-1).to(device=device, dtype=torch.int64)
+            ops.eval_accumulate("ce", output, tgt, 1, seg, None, None, 0.0, scratch, None, p0[at:at + n].view(1, n))
+        labels.append(np.asarray(target).reshape(-1))
+        shots.append(np.asarray(shot_num).reshape(-1))
+        at += n
+    cat = lambda xs: np.concatenate(xs) if xs else np.array([])                           # noqa: E731
+    return cat(labels).astype(np.float64), cat(shots).astype(np.float64), p0[:at].cpu().numpy().astype(np.float64)   # ONE read-back
+
+
+def evaluate_detail(train_loader: DataLoader, valid_loader: DataLoader, test_loader: DataLoader, model: torch.nn.Module,
+                    device: Optional[str] = "cpu", save_csv: Optional[str] = None, tag: Optional[str] = None,
+                    model_type: Literal["single", "multi", "multi-GB"] = "single"):
+    """Reference :242-350: the CSV ``task, label, shot, pred, tag`` (pred = softmax column 0, the disruption probability) over the
+    three loaders, whose datasets are switched to ``get_shot_num = True``.  Returns the frame (the reference returns nothing)."""
+    import pandas as pd
+    for loader in (train_loader, valid_loader, test_loader):
+        loader.dataset.get_shot_num = True
+    if device is None:
+        device = torch.device("cuda:0")
+    model.to(device)
+    model.eval()
+    task, label, shot, pred = [], [], [], []
+    for name, loader in (("train", train_loader), ("valid", valid_loader), ("test", test_loader)):
+        lb, sh, p = _loader_probabilities(loader, model, device, model_type)
+        label.append(lb); shot.append(sh); pred.append(p)
+        task.extend([name for _ in range(len(loader.dataset))])
+    df = pd.DataFrame({})
+    df['task'] = task
+    df['label'] = np.concatenate(label)
+    df['shot'] = np.concatenate(shot).astype(int)
+    df['pred'] = np.concatenate(pred)
+    df['tag'] = [tag for _ in range(len(df['pred']))]
+    if save_csv:
+        df.to_csv(save_csv, index=False)
+    return df

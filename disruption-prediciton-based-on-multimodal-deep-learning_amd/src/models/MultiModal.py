@@ -76,6 +76,15 @@ class MultiModalModel(nn.Module):
         x = torch.cat([self.encoder_video(x_video), self.encoder_0D(x_0D)], axis=1)
         return _classifier(_connector(x, self.connector), self.classifier)
 
+    def encode_video(self, x_video: torch.Tensor):
+        """The video latent ``forward`` concatenates; with ``forward_from_video_latent`` it lets an analysis that varies only the
+        0D input (src/_importance.py) run the video encoder once per sample."""
+        return self.encoder_video(x_video)
+
+    def forward_from_video_latent(self, vis_latent: torch.Tensor, x_0D: torch.Tensor):
+        x = torch.cat([vis_latent, self.encoder_0D(x_0D)], axis=1)
+        return _classifier(_connector(x, self.connector), self.classifier)
+
     def encode(self, x_vis: torch.Tensor, x_0D: torch.Tensor):
         with torch.no_grad():
             h_vis = self.encoder_video(x_vis)
@@ -137,6 +146,21 @@ class MultiModalModel_GB(nn.Module):
         out_multi = _classifier(x, self.classifier)
         return out_multi if self.use_stream == 'multi' else (out_multi, out_vis, out_ts)
 
+    def encode_video(self, x_vis: torch.Tensor):
+        """See MultiModalModel.encode_video."""
+        return self.vis_model._encode(x_vis)
+
+    def forward_from_video_latent(self, vis_latent: torch.Tensor, x_ts: torch.Tensor):
+        """``forward_stream`` of the two-stream modes from a video latent computed earlier (the single-stream modes need no latent)."""
+        if self.use_stream in ("video", "0D"):
+            raise RuntimeError("forward_from_video_latent: use_stream is %r; only 'multi' and 'multi-GB' fuse a video latent" % self.use_stream)
+        ts_latent = self.ts_model.encoder(x_ts)
+        out_vis = self.vis_model._head(vis_latent)
+        out_ts = self.ts_model._head(ts_latent)
+        x = _connector(torch.cat([vis_latent, ts_latent], axis=1), self.connector)
+        out_multi = _classifier(x, self.classifier)
+        return out_multi if self.use_stream == 'multi' else (out_multi, out_vis, out_ts)
+
     def encode(self, x_vis: torch.Tensor, x_0D: torch.Tensor):
         with torch.no_grad():
             vis_latent, ts_latent = self._both(x_vis, x_0D)
@@ -174,6 +198,14 @@ class TFN(nn.Module):
 
     def forward(self, x_vis: torch.Tensor, x_0D: torch.Tensor):
         fusion = OuterFusionFunction.apply(self.encoder_video(x_vis), self.encoder_0D(x_0D))
+        return _classifier(_connector(fusion, self.connector), self.classifier)
+
+    def encode_video(self, x_vis: torch.Tensor):
+        """See MultiModalModel.encode_video."""
+        return self.encoder_video(x_vis)
+
+    def forward_from_video_latent(self, vis_latent: torch.Tensor, x_0D: torch.Tensor):
+        fusion = OuterFusionFunction.apply(vis_latent, self.encoder_0D(x_0D))
         return _classifier(_connector(fusion, self.connector), self.classifier)
 
     def encode(self, x_vis: torch.Tensor, x_0D: torch.Tensor):
@@ -221,6 +253,20 @@ class TFN_GB(nn.Module):
         h_0D = ts.encoder(x_0D)
         self.h_vis = (h_vis.detach(),)                 # values only (see vis_latent)
         self.h_0D = (h_0D.detach(),)
+        out_vis = vis._head(h_vis)
+        out_0D = ts._head(h_0D)
+        fusion = dropout(OuterFusionFunction.apply(h_vis, h_0D), self.dropout.p, self.dropout.training)
+        bn = self.classifier[1]
+        h = linear_bn_leaky(fusion, self.classifier[0], bn, 0.0, bn.training)
+        return (_lin(h, self.classifier[3]), out_vis, out_0D)
+
+    def encode_video(self, x_vis: torch.Tensor):
+        """See MultiModalModel.encode_video."""
+        return self.embedd_subnet['network_video']._encode(x_vis)
+
+    def forward_from_video_latent(self, h_vis: torch.Tensor, x_0D: torch.Tensor):
+        vis, ts = self.embedd_subnet['network_video'], self.embedd_subnet['network_0D']
+        h_0D = ts.encoder(x_0D)
         out_vis = vis._head(h_vis)
         out_0D = ts._head(h_0D)
         fusion = dropout(OuterFusionFunction.apply(h_vis, h_0D), self.dropout.p, self.dropout.training)

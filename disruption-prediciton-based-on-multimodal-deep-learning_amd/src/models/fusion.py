@@ -96,6 +96,20 @@ class FusionGB(nn.Module):
         out_multi = _classifier(x, self.classifier)
         return out_multi if self.use_stream == 'multi' else (out_multi, out_vis, out_ts)
 
+    def encode_video(self, x_vis: torch.Tensor):
+        """The video latent of ``forward_stream``; see MultiModalModel.encode_video."""
+        return self._vis[0](x_vis)
+
+    def forward_from_video_latent(self, vis_latent: torch.Tensor, x_ts: torch.Tensor):
+        """``forward_stream`` of the two-stream modes from a video latent computed earlier (src/_importance.py)."""
+        if self.use_stream in ("video", "0D"):
+            raise RuntimeError("forward_from_video_latent: use_stream is %r; only 'multi' and 'multi-GB' fuse a video latent" % self.use_stream)
+        ts_latent, out_ts = self._ts_eager(x_ts)
+        out_vis = self._vis[1](vis_latent)
+        x = _connector(torch.cat([vis_latent, ts_latent], axis=1), self.connector)
+        out_multi = _classifier(x, self.classifier)
+        return out_multi if self.use_stream == 'multi' else (out_multi, out_vis, out_ts)
+
     def _ts_eager(self, x_ts: torch.Tensor):
         ts_latent = self._ts[0](x_ts)
         return ts_latent, self._ts[1](ts_latent)

@@ -462,3 +462,43 @@ def softmax_loss(kind: str, logits: torch.Tensor, target: torch.Tensor, weight: 
     N.check(N.lib().md_softmax_loss(KIND[kind], _p(logits), _p(target), B, K, _p(weight), _p(margins), float(gamma_or_s),
                                     _p(loss), _p(dl), _p(pred), _stream()), "md_softmax_loss")
     return loss, dl, pred
+
+
+def window_gather(table: torch.Tensor, start: torch.Tensor, seq_len: int, tau: int, perms: Optional[torch.Tensor],
+                  colperm: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[v, i, t, f] = table[p_{v,f}(start[i] + t*tau), f] (md_window_gather).  table (R, F) fp32, start (n) int64,
+    perms (P, R) int32 or None, colperm (V, F) int32 with -1 = column not permuted.  The caller has checked the starts."""
+    require_cuda(table, start, perms, colperm); f32(table)
+    if start.dtype != torch.int64 or colperm.dtype != torch.int32 or (perms is not None and perms.dtype != torch.int32):
+        raise RuntimeError("window_gather: start is int64, perms and colperm are int32")
+    R, F = table.shape
+    V, n = colperm.shape[0], start.shape[0]
+    if colperm.shape[1] != F or (perms is not None and perms.shape[1] != R):
+        raise RuntimeError("window_gather: colperm is (V, F) and perms is (P, R)")
+    if out is None:
+        out = torch.empty((V, n, seq_len, F), device=table.device, dtype=torch.float32)
+    elif out.shape != (V, n, seq_len, F) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError("window_gather: out must be a contiguous (V, n, T, F) fp32 device tensor")
+    P = 0 if perms is None else perms.shape[0]
+    N.check(N.lib().md_window_gather(_p(table), R, F, _p(start), n, int(seq_len), int(tau), _p(perms), P, _p(colperm), V, _p(out),
+                                     _stream()), "md_window_gather")
+    return out
+
+
+def eval_accumulate(kind: str, logits: torch.Tensor, target: torch.Tensor, n_variants: int, seg: torch.Tensor,
+                    weight: Optional[torch.Tensor], margins: Optional[torch.Tensor], gamma_or_s: float, loss: torch.Tensor,
+                    confusion: Optional[torch.Tensor], p0: Optional[torch.Tensor] = None) -> None:
+    """md_eval_accumulate: logits (V*n, K) -> loss[v, s] (a (V, >= S) fp32 view whose rows are ``loss.stride(0)`` apart),
+    confusion (V, K, K) int32 added to, p0 (V, n) softmax column 0.  seg (S+1) int32 sample offsets of the loader's batches."""
+    require_cuda(logits, target, seg, weight, margins, confusion, p0); f32(logits)
+    if target.dtype != torch.int64 or seg.dtype != torch.int32 or (confusion is not None and confusion.dtype != torch.int32):
+        raise RuntimeError("eval_accumulate: target is int64, seg and confusion are int32")
+    V, n, K, S = int(n_variants), target.shape[0], logits.shape[1], seg.shape[0] - 1
+    if logits.shape[0] != V * n or not loss.is_cuda or loss.dtype != torch.float32 or loss.dim() != 2 or loss.shape[0] != V \
+            or loss.shape[1] < S or loss.stride(1) != 1:
+        raise RuntimeError("eval_accumulate: logits is (V*n, K) and loss a (V, >= S) fp32 device view with unit column stride")
+    if (confusion is not None and confusion.shape != (V, K, K)) or (p0 is not None and (p0.shape != (V, n) or p0.dtype != torch.float32)):
+        raise RuntimeError("eval_accumulate: confusion is (V, K, K) and p0 is (V, n) fp32")
+    N.check(N.lib().md_eval_accumulate(KIND[kind], _p(logits), _p(target), V, n, K, _p(seg), S, _p(weight), _p(margins),
+                                       float(gamma_or_s), _p(loss), loss.stride(0) if V > 1 else max(S, loss.stride(0)),
+                                       _p(confusion), _p(p0), _stream()), "md_eval_accumulate")

@@ -685,6 +685,24 @@ size_t md_tsmm_mtw_scratch_doubles(int64_t rows, int32_t D, int32_t E);
 int md_tsmm_mtw(const float* M, int64_t rows, int32_t D, const float* mean, const float* extra, int32_t E, const float* W,
                 float* out_f32, double* out_f64, double* scratch, void* stream);
 
+/* ---- Permutation feature importance of the 0D signals (csrc/importance.hip; reference src/feature_importance.py:29-134).
+ * md_window_gather: out[V][n][T][F], out[v][i][t][f] = table[p(start[i] + t*tau)][f] with p = row colperm[v][f] of perms, or the
+ * identity where colperm[v][f] = -1.  table [R][F] fp32 row-major; start [n] int64 row positions; perms [P][R] int32 (may be NULL
+ * when P = 0); colperm [V][F] int32.  The caller guarantees 0 <= start[i] and start[i] + (T-1)*tau < R (a row outside the table,
+ * before or after the permutation, reads as 0).  Pure data movement: bit-exact. */
+int md_window_gather(const float* table, int64_t R, int32_t F, const int64_t* start, int32_t n, int32_t T, int32_t tau,
+                     const int32_t* perms, int32_t P, const int32_t* colperm, int32_t V, float* out, void* stream);
+/* md_eval_accumulate: what compute_loss (:29-71) keeps, for V variants of n samples at once.  logits [V*n][K] fp32, K <= 8;
+ * target [n] int64, shared by the variants; seg [S+1] int32 increasing sample offsets, segment s = one batch of the loader.
+ * kind / class_weight / margins / gamma_or_s as md_softmax_loss (same per-sample arithmetic, csrc/softmax_loss.h).
+ *   loss[v*loss_stride + s] = the value the loss module returns for that batch (Focal, CE: sum; LDAM: sum w ce / sum w);
+ *   confusion[v][K][K] (int32, [target][arg-max], may be NULL) is ADDED to, so it accumulates across launches;
+ *   p0[v*n + i] (may be NULL) = softmax(logits)[:, 0].
+ * One workgroup per (segment, variant); the reduction order is fixed (no floating-point atomics).  V <= 65535. */
+int md_eval_accumulate(int32_t kind, const float* logits, const int64_t* target, int32_t V, int32_t n, int32_t K,
+                       const int32_t* seg, int32_t S, const float* class_weight, const float* margins, float gamma_or_s,
+                       float* loss, int64_t loss_stride, int32_t* confusion, float* p0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
