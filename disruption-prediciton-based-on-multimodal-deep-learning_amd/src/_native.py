@@ -204,6 +204,11 @@ SIGNATURES = {
     "md_tsmm_mtw": (C.c_int, [_P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "md_window_gather": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P]),
     "md_eval_accumulate": (C.c_int, [_I32, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _F, _P, _I64, _P, _P, _P]),
+    "md_sym_eig": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P]),
+    "md_cca_workspace_floats": (_SZ, [_I32, _I32, _I32]),
+    "md_cca_workspace_offset": (_I64, [_I32, _I32, _I32, _I32]),
+    "md_cca_loss_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _P, _P, _P]),
+    "md_cca_loss_bwd": (C.c_int, [_P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
 }
 
 ERRORS = {-1: "bad shape", -2: "unsupported", -3: "workspace", -4: "kernel launch failed", -5: "null pointer"}

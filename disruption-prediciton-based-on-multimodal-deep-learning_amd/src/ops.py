@@ -502,3 +502,65 @@ def eval_accumulate(kind: str, logits: torch.Tensor, target: torch.Tensor, n_var
     N.check(N.lib().md_eval_accumulate(KIND[kind], _p(logits), _p(target), V, n, K, _p(seg), S, _p(weight), _p(margins),
                                        float(gamma_or_s), _p(loss), loss.stride(0) if V > 1 else max(S, loss.stride(0)),
                                        _p(confusion), _p(p0), _stream()), "md_eval_accumulate")
+
+
+CCA_MAX_O = 128
+
+
+def sym_eig(a: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """md_sym_eig: a (n, n) or (batch, n, n) symmetric fp32, n <= 128 -> (w ascending, v with the eigenvectors as columns,
+    sweeps int32 per matrix).  One workgroup per matrix, no host synchronisation."""
+    require_cuda(a); f32(a)
+    if a.dim() not in (2, 3) or a.shape[-1] != a.shape[-2] or a.shape[-1] < 1:
+        raise RuntimeError("sym_eig: a is (n, n) or (batch, n, n)")
+    n = a.shape[-1]
+    if n > CCA_MAX_O:
+        raise ValueError("sym_eig: n = %d is above the limit of %d" % (n, CCA_MAX_O))
+    batch = 1 if a.dim() == 2 else a.shape[0]
+    w = torch.empty(a.shape[:-1], device=a.device, dtype=torch.float32)
+    v = torch.empty_like(a)
+    sweeps = torch.empty(batch, device=a.device, dtype=torch.int32)
+    N.check(N.lib().md_sym_eig(_p(a), batch, n, _p(w), _p(v), _p(sweeps), _stream()), "md_sym_eig")
+    return w, v, sweeps
+
+
+def cca_workspace(m: int, o1: int, o2: int, device) -> torch.Tensor:
+    n = int(N.lib().md_cca_workspace_floats(m, o1, o2))
+    if n == 0:
+        raise RuntimeError("cca_loss: bad shape (m >= 2, 1 <= o1, o2 <= %d)" % CCA_MAX_O)
+    return torch.empty(n, device=device, dtype=torch.float32)
+
+
+def cca_workspace_view(ws: torch.Tensor, m: int, o1: int, o2: int, what: str) -> torch.Tensor:
+    """A view of what md_cca_loss_fwd left in its workspace: 'lam' eigenvalues of T^T T + rho I (o2, ascending), 'sweeps' (3 int32:
+    S11, S22, T^T T), 'T' (o1, o2), 'd1' (o1), 'd2' (o2)."""
+    which, shape = {"lam": (0, (o2,)), "sweeps": (1, (3,)), "T": (2, (o1, o2)), "d1": (3, (o1,)), "d2": (4, (o2,))}[what]
+    off = int(N.lib().md_cca_workspace_offset(m, o1, o2, which))
+    count = 1
+    for s in shape:
+        count *= s
+    out = ws[off:off + count]
+    return out.view(torch.int32) if what == "sweeps" else out.view(shape)
+
+
+def cca_loss_fwd(h1: torch.Tensor, h2: torch.Tensor, k: int, r1: float, r2: float, eps: float):
+    """md_cca_loss_fwd: h1 (m, o1), h2 (m, o2) -> (loss[1], workspace).  k = 0: all singular values."""
+    require_cuda(h1, h2); f32(h1); f32(h2)
+    if h1.dim() != 2 or h2.dim() != 2 or h1.shape[0] != h2.shape[0]:
+        raise RuntimeError("cca_loss: h1 is (m, o1) and h2 is (m, o2)")
+    m, o1, o2 = h1.shape[0], h1.shape[1], h2.shape[1]
+    ws = cca_workspace(m, o1, o2, h1.device)
+    loss = torch.empty(1, device=h1.device, dtype=torch.float32)
+    N.check(N.lib().md_cca_loss_fwd(_p(h1), _p(h2), m, o1, o2, int(k), float(r1), float(r2), float(eps), _p(ws), _p(loss),
+                                    _stream()), "md_cca_loss_fwd")
+    return loss, ws
+
+
+def cca_loss_bwd(grad_out: torch.Tensor, ws: torch.Tensor, m: int, o1: int, o2: int, k: int, eps: float):
+    """md_cca_loss_bwd: grad_out a one-element fp32 device tensor -> (dh1 (m, o1), dh2 (m, o2))."""
+    require_cuda(grad_out, ws); f32(grad_out)
+    dh1 = torch.empty((m, o1), device=ws.device, dtype=torch.float32)
+    dh2 = torch.empty((m, o2), device=ws.device, dtype=torch.float32)
+    N.check(N.lib().md_cca_loss_bwd(_p(grad_out), m, o1, o2, int(k), float(eps), _p(ws), _p(dh1), _p(dh2), _stream()),
+            "md_cca_loss_bwd")
+    return dh1, dh2

@@ -703,6 +703,32 @@ int md_eval_accumulate(int32_t kind, const float* logits, const int64_t* target,
                        const int32_t* seg, int32_t S, const float* class_weight, const float* margins, float gamma_or_s,
                        float* loss, int64_t loss_stride, int32_t* confusion, float* p0, void* stream);
 
+/* ---- Deep CCA (csrc/cca.hip; reference src/CCA.py:25-83).  Fixed launch counts, no atomics: the same input gives the same bits.
+ * Widths above MD_CCA_MAX_O are refused with MD_ERR_UNSUPPORTED. */
+#define MD_CCA_MAX_O 128
+/* Eigendecomposition of `batch` symmetric fp32 matrices a[batch][n][n], 1 <= n <= 128, one workgroup each, the matrix and the
+ * vectors held in LDS (parallel-order cyclic Jacobi; ends when a whole sweep finds every off-diagonal negligible against the
+ * geometric mean of its two diagonal entries, at most 30 sweeps).  w[batch][n] ascending; v[batch][n][n] has the eigenvectors as
+ * COLUMNS in the order of w, the largest-magnitude component of each positive (equal magnitudes: the lowest row decides).
+ * sweeps_out[batch] (may be NULL) = sweeps run, the rotation-free ones that end the two tolerance stages included (a diagonal input: 2);
+ * 30 means the cap ended it. */
+int md_sym_eig(const float* a, int32_t batch, int32_t n, float* w, float* v, int32_t* sweeps_out, void* stream);
+/* CCA loss of two views h1 (m, o1), h2 (m, o2) row-major, m >= 2, 1 <= o1, o2 <= 128 (CCALoss.forward :35-83):
+ *   loss[0] = -sum of the k largest singular values of T = S11^-1/2 S12 S22^-1/2 taken as sqrt(max(eig(T^T T + r1 I), eps)) (k >= 1,
+ *   the reference's top-k branch), or -(nuclear norm of T) for k = 0 (all singular values).  S11 = H1^T H1 / (m-1) + r1 I on the
+ *   centred views (fp64-accumulated), eigenvalues <= eps of S11 / S22 discarded.  9 launches.
+ * md_cca_loss_bwd: the closed-form gradient from what the forward left in the workspace (eigenpairs, T, the whitening factors;
+ * nothing is recomputed): dh1 (m, o1), dh2 (m, o2) = grad_out[0] * d loss / d h.  grad_out is a DEVICE scalar.  9 launches.
+ * workspace: md_cca_workspace_floats floats, the same buffer for both calls.  md_cca_workspace_offset gives the float offset of
+ * what a caller may want to look at: which = 0 eigenvalues of T^T T + rho I (o2, ascending), 1 sweep counts (3 x int32: S11, S22,
+ * T^T T), 2 T (o1, o2), 3 eigenvalues of S11 (o1), 4 eigenvalues of S22 (o2); -1 for anything else. */
+size_t md_cca_workspace_floats(int32_t m, int32_t o1, int32_t o2);
+int64_t md_cca_workspace_offset(int32_t m, int32_t o1, int32_t o2, int32_t which);
+int md_cca_loss_fwd(const float* h1, const float* h2, int32_t m, int32_t o1, int32_t o2, int32_t k, float r1, float r2, float eps,
+                    float* workspace, float* loss, void* stream);
+int md_cca_loss_bwd(const float* grad_out, int32_t m, int32_t o1, int32_t o2, int32_t k, float eps, float* workspace, float* dh1,
+                    float* dh2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
